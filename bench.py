@@ -24,9 +24,14 @@ The engine thread itself brackets the window: after W*G iterations of the steady
 barrier and records t0, after K*G more again sync + barrier and t1, so exactly K steps (K*G iterations) are timed
 on every rank. Output tokens = tokens the engine generated inside the window; TTFT = client-side time from
 sending the request to the first content chunk, over requests whose first token arrived inside the window.
-The JSON reports the window's engine iterations, prompt (prefill) tokens, output tokens and TTFT sample count;
-rank 0 exits non-zero when fewer than 32 TTFT samples fell in the window (a window that timed no prefill).
+The JSON reports the window's engine iterations, prompt (prefill) tokens, output tokens and TTFT sample count.
 value = sum over ranks of tokens / max over ranks of window. Rank 0 prints one JSON line.
+
+A plain run does what that line needs and no more: load, tune, capture, one load phase with the reference's
+sampling defaults, the window. `--full` adds the rest: a second load phase with greedy sampling on the same
+server (`config.other_phases`), and rank 0 exits 3 when fewer than 32 TTFT samples fell in the window (a
+window that timed no prefill; a plain run only warns). `--dump-outputs DIR` writes DIR/logits.npy after the
+timed steps (dump_outputs below).
 """
 from __future__ import annotations
 
@@ -40,14 +45,21 @@ import tempfile
 import threading
 import time
 
-import numpy as np
-import torch
+T_PROC = time.time()  # before the heavy imports: config.timeline_s counts from here
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 METRIC = "output tokens/sec + p50 TTFT, /v1/chat/completions Llama-3-8B Q4_K at 1/2/4/8 MI355X"
 TEMPLATE_OVERHEAD = 24  # Llama-3 chat template tokens around one user message (ByteTokenizer)
+TIMELINE: dict = {}  # seconds since process start at which each part of the run was over (config.timeline_s)
+
+
+def mark(name: str):
+    TIMELINE[name] = round(time.time() - T_PROC, 2)
 
 
 def parse():
@@ -58,7 +70,8 @@ def parse():
     ap.add_argument("--step-group", type=int, default=16,
                     help="engine iterations per bench step (G): K steps time K*G continuous-batching iterations")
     ap.add_argument("--min-ttft-samples", type=int, default=32,
-                    help="rank 0 exits non-zero if fewer TTFT samples fall in the window (0: no check)")
+                    help="rank 0 warns (with --full: exits non-zero) if fewer TTFT samples fall in the window "
+                         "(0: no check)")
     ap.add_argument("--model", default="llama3-8b", choices=["llama3-8b", "llama3-70b", "llama32-1b", "qwen3-30b-a3b", "qwen3-8b"],
                     help="qwen3-30b-a3b: the gallery's first entry (128 experts, 8 active) on the MoE path")
     ap.add_argument("--path", default="http", choices=["http", "engine"])
@@ -92,11 +105,25 @@ def parse():
     ap.add_argument("--tokenizer", default="bpe", choices=["bpe", "byte"],
                     help="bpe: a synthetic Llama-3-sized byte-level BPE vocabulary (128,256 ids, tokenizer/synth_bpe.py) "
                          "served through the GGUF BPE tokenizer; byte: one token per byte (no detokenisation work)")
-    ap.add_argument("--phases", default="reference,greedy",
+    ap.add_argument("--phases", default=None,
                     help="comma list of sampling phases measured back to back on the same server: reference = "
                          "the reference's defaults (temperature 0.9, top_k 40, top_p 0.95; backend_config.go "
-                         "SetDefaults) on the GPU sampler; greedy = argmax. The first phase is the headline")
-    return ap.parse_args()
+                         "SetDefaults) on the GPU sampler; greedy = argmax. The first phase is the headline "
+                         "(default: reference; with --full: reference,greedy)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the greedy phase after the headline phase (HTTP "
+                         "path) and the exit status 3 for a window with fewer than --min-ttft-samples TTFT samples")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the probe batch's logits to DIR/logits.npy (see dump_outputs)")
+    args = ap.parse_args()
+    if args.phases is None:
+        args.phases = "reference,greedy" if args.full else "reference"
+    if args.dump_outputs and args.tp > 1:
+        raise SystemExit("--dump-outputs runs on one rank's engine (no --tp)")
+    if args.dump_outputs and args.phases.split(",")[0] == "greedy":
+        raise SystemExit("--dump-outputs records the logits the sampler receives; a greedy headline phase takes its "
+                         "ids from the step's argmax head instead (see dump_outputs)")
+    return args
 
 
 SAMPLING = {"reference": {"temperature": 0.9, "top_k": 40, "top_p": 0.95},
@@ -128,6 +155,97 @@ def prompt_sizing(tok, prompt_len: int):
     sample = " ".join(rng.choice(WORDS, size=2000))
     per_word = len(tok.encode(sample, add_special=False)) / 2000.0
     return overhead, max(1, int(round((prompt_len - overhead) / per_word)))
+
+
+def generated_ahead(src, workers: int = 8):
+    """The synthetic source with every tensor drawn ahead of the loader on a thread pool (numpy's generators
+    release the GIL). Each tensor's bytes depend on its name and the seed alone, so the model is the same; the
+    load no longer waits for one core to draw 5 GB of random blocks between its uploads."""
+    import concurrent.futures as cf
+    last = "token_embd.weight"  # first in the plan, read last by the loader
+    names = [n for n in src.plan if n != last] + [n for n in src.plan if n == last]
+    ex = cf.ThreadPoolExecutor(workers)
+    ahead = {n: ex.submit(src, n) for n in names}
+    ex.shutdown(wait=False)
+
+    def get_tensor(name):
+        f = ahead.pop(name, None)
+        return f.result() if f is not None else src(name)
+
+    get_tensor.plan = src.plan
+    return get_tensor
+
+
+def prompt_maker(args, tok, rng):
+    """() -> token ids of one chat request (~--prompt-len tokens after the chat template), drawn from `rng`."""
+    from localai_tfp_amd.templates.chat import render_chat
+    from localai_tfp_amd.tools.loadgen import WORDS as words
+    n_words = None if args.tokenizer == "byte" else prompt_sizing(tok, args.prompt_len)[1]
+
+    def make_prompt():
+        if n_words is None:
+            body = " ".join(rng.choice(words, size=args.prompt_len))[: max(1, args.prompt_len - TEMPLATE_OVERHEAD)]
+        else:
+            body = " ".join(rng.choice(words, size=n_words))
+        return tok.encode(render_chat([{"role": "user", "content": body}], tok))
+
+    return make_prompt
+
+
+DUMP_COLUMNS = 8192  # vocabulary columns kept per row (a fixed seeded sample: 128 rows x 8192 x fp32 = 4 MB)
+
+
+def dump_outputs(args, eng, tok, phase, out_dir):
+    """--dump-outputs: what the timed path computes for a fixed batch, as DIR/logits.npy (float32).
+
+    The rows of the window's own last step are whichever requests the closed-loop clients had in flight at
+    that moment, so they differ from run to run. Once the timed steps are over, the same engine (weights, tuned
+    GEMM plans, step graphs, sampler of the headline phase) therefore serves one more batch that is the same in
+    every run: --concurrency chat prompts from a fixed seed, submitted together, one token each. The engine
+    steps through them exactly as it stepped inside the window (continuous batching, chunked prefill), and the
+    logits row each request's token is sampled from, as the sampler receives it, is kept: logits.npy is
+    [request, column] over a fixed seeded sample of DUMP_COLUMNS vocabulary columns. Logits rather than
+    the sampled ids: at temperature 0.9 an id flips on a last-bit difference of its row, which no tolerance
+    covers. A greedy headline phase takes its ids from the step's argmax head and never hands logits to the
+    sampler: nothing could be recorded then, so such a run is refused when it starts."""
+    from localai_tfp_amd.engine.sequence import Request
+    from localai_tfp_amd.ops.sampling import SamplingParams
+    for rid in list(eng.seqs):  # engine path: the requests still running when the window closed
+        eng.abort(rid)
+    eng.run_until_done()
+    make_prompt = prompt_maker(args, tok, np.random.default_rng(4321))
+    n, V = args.concurrency, eng.model.cfg.vocab
+    cols = np.sort(np.random.default_rng(99).choice(V, size=min(V, DUMP_COLUMNS), replace=False))
+    cols_dev = torch.from_numpy(cols).to(eng.device)
+    logits = np.zeros((n, len(cols)), np.float32)
+    row_of, seen = {}, set()
+    sample = eng.sampler.sample
+
+    def tap(lg, params, histories, steps, *a, **kw):
+        rows = lg[:len(params)].index_select(1, cols_dev).float().cpu().numpy()  # before the sampler edits lg
+        for r, p in enumerate(params):
+            i = row_of.get(id(p))
+            if i is not None and steps[r] == 0:
+                logits[i] = rows[r]
+                seen.add(i)
+        return sample(lg, params, histories, steps, *a, **kw)
+
+    sp = {k: v for k, v in SAMPLING[phase].items() if k != "json"}
+    # no prefix reuse: every probe row is computed in this batch, not taken from the KV blocks an earlier request left
+    reqs = [Request(make_prompt(), SamplingParams(**sp, ignore_eos=True), max_tokens=1, cache_prompt=False)
+            for _ in range(n)]
+    row_of.update({id(r.params): i for i, r in enumerate(reqs)})
+    eng.sampler.sample = tap
+    try:
+        for r in reqs:
+            eng.submit(r)
+        eng.run_until_done()
+    finally:
+        del eng.sampler.sample
+    if len(seen) != n:
+        raise SystemExit(f"--dump-outputs: the sampler saw {len(seen)} of {n} probe rows (phase {phase})")
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "logits.npy"), logits)
 
 
 class _GroupSync:
@@ -232,6 +350,7 @@ def main():
     from localai_tfp_amd.models.llama import LlamaModel
     from localai_tfp_amd.models.synthetic import synthetic_source
     from localai_tfp_amd.tokenizer import ByteTokenizer
+    mark("imports")
 
     cfg = {"llama3-8b": C.LLAMA3_8B, "llama3-70b": C.LLAMA3_70B, "llama32-1b": C.LLAMA32_1B,
            "qwen3-30b-a3b": C.QWEN3_30B_A3B, "qwen3-8b": C.QWEN3_8B}[args.model]
@@ -263,12 +382,16 @@ def main():
     src = synthetic_source(cfg, args.ftype, seed=1, shard_gen=tp > 1 or rehearsal > 1)
     if rehearsal > 1:
         model = LlamaModel.load(cfg, src, dev, 0, rehearsal, None)
+    elif tp == 1:
+        model = LlamaModel.load(cfg, generated_ahead(src), dev)
     else:
         model = LlamaModel.load(cfg, src, dev, rank % tp, tp, tp_group)
     t_load = time.time() - t0
+    mark("load")
     if args.tokenizer == "bpe" and cfg.vocab != 128256:  # CPU plumbing model / other vocabularies
         args.tokenizer = "byte"
     tok = make_tokenizer(args.tokenizer, cfg.vocab)
+    mark("tokenizer")
     ecfg = EngineConfig(max_num_seqs=args.concurrency, max_batched_tokens=args.max_batched_tokens,
                         prefill_chunk=args.prefill_chunk or None,
                         max_model_len=max(4096, args.prompt_len + args.gen_len + 64), use_graphs=not args.no_graphs,
@@ -276,6 +399,7 @@ def main():
     if dev.type == "cpu":
         ecfg.num_blocks = 2048
     eng = LLMEngine(model, tok, ecfg, tp=link)
+    mark("engine")
     if link is not None and not link.is_leader:
         eng.follow()  # replay the leader's plans until it stops the engine
         link.close()
@@ -285,11 +409,18 @@ def main():
     t0 = time.time()
     n_graphs = eng.precapture_graphs()
     t_capture = time.time() - t0
+    mark("capture")
 
     if args.path == "http":
         res = run_http(args, eng, tok, cfg, dev, dist)
     else:
         res = run_engine(args, eng, tok, dev, dist)
+    mark("serving")
+    st = _host_snapshot(eng)  # the serving run's counters (the probe batch of --dump-outputs adds its own steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args, eng, tok, args.phases.split(",")[0], args.dump_outputs)
+        mark("dump")
+    if args.path != "http":
         eng.shutdown()  # tensor parallel: releases the followers from engine.follow()
     t_el, tokens, ttfts, extra = res[0]
     bad_window = False
@@ -321,7 +452,6 @@ def main():
     # 16-bit MFMA operands (Q4_K_M weights dequantised in-register), fp32 accumulation everywhere
     act_name = "fp16" if ACT_DTYPE == torch.float16 else "bf16"
     if rank == 0:
-        st = eng.stats
         out = {
             "metric": METRIC,
             "value": round(value, 2),
@@ -352,11 +482,11 @@ def main():
                     "gateway_workers": args.gateway_workers or (world if args.dp_gateway == "single" and world > 1 else 1)}
                    if args.path == "http" else {}),
                 "load_s": round(t_load, 1), "gemm_tune_s": round(getattr(eng, "stats_tune_s", 0.0), 1),
-                "graph_capture_s": round(t_capture, 1), "graphs": n_graphs,
+                "graph_capture_s": round(t_capture, 1), "graphs": n_graphs, "timeline_s": TIMELINE,
                 "graph_steps": st["graph_steps"], "total_steps": st["steps"],
                 "host_ms_per_step": {k[:-2]: round(st[k] / max(1, st["steps"]) * 1e3, 3)
                                      for k in ("sched_s", "plan_s", "fwd_s", "wait_s", "process_s")},
-                "graph_replay_host_ms": round(sum(g.replay_s for g in eng.graphs.values()) / max(1, st["graph_steps"]) * 1e3, 3),
+                "graph_replay_host_ms": round(st["replay_s"] / max(1, st["graph_steps"]) * 1e3, 3),
                 "weights_gb": round(model.weight_bytes() / 1e9, 2),
                 "dense_weight_copy_gb": round(model.dense_cache_bytes() / 1e9, 2) if hasattr(model, "dense_cache_bytes") else 0.0, "kv_blocks": eng.kv.num_blocks,
                 "kv_dtype": args.kv_dtype,
@@ -374,7 +504,7 @@ def main():
         if args.min_ttft_samples and n_tt is not None and n_tt < args.min_ttft_samples and not rehearsal:
             print(f"[bench] only {n_tt} TTFT samples fell in the timed window (< {args.min_ttft_samples}): the window "
                   "did not time a representative serving mix", file=sys.stderr, flush=True)
-            bad_window = True
+            bad_window = args.full  # a plain run reports the count and the warning; --full fails on it
         if eng.trace is not None:
             torch.cuda.synchronize() if dev.type == "cuda" else None
             ev = eng.trace_events[-(args.steps * args.step_group + 50):]
@@ -391,6 +521,9 @@ def main():
     if world > 1:
         import torch.distributed as tdist
         tdist.destroy_process_group()
+    mark("exit")
+    if rank == 0:
+        print(f"[bench] timeline_s {TIMELINE}", file=sys.stderr, flush=True)
     if bad_window:
         sys.exit(3)
 
@@ -507,6 +640,7 @@ def run_http(args, eng, tok, cfg, dev, dist):
     try:
         if front:
             wait_http(f"http://127.0.0.1:{port}/readyz", 120, gw)
+        mark("gateway")
         for pi, phase in enumerate(args.phases.split(",")):
             sp = SAMPLING[phase]
             samp_args = ["--temperature", str(sp["temperature"])]
@@ -550,6 +684,7 @@ def run_http(args, eng, tok, cfg, dev, dist):
                     except subprocess.TimeoutExpired:
                         lg.kill()
             out.append(_http_phase_result(win, rec_paths))
+            mark(f"window_{phase}")
             # the cancelled streams of this phase must leave the engine before the next phase's gate counts
             t_d = time.time()
             while (eng.sched.running or eng.sched.waiting) and time.time() - t_d < 120:
@@ -602,22 +737,7 @@ def _http_phase_result(win, rec_paths):
 def run_engine(args, eng, tok, dev, dist):
     from localai_tfp_amd.engine.sequence import Request
     from localai_tfp_amd.ops.sampling import SamplingParams
-    from localai_tfp_amd.templates.chat import render_chat
-    rng = np.random.default_rng(1234 + int(os.environ.get("RANK", "0")))
-    from localai_tfp_amd.tools.loadgen import WORDS as words
-
-    if args.tokenizer == "byte":
-        n_words = None
-    else:
-        _, n_words = prompt_sizing(tok, args.prompt_len)
-
-    def make_prompt():
-        if n_words is None:
-            body = " ".join(rng.choice(words, size=args.prompt_len))[: max(1, args.prompt_len - TEMPLATE_OVERHEAD)]
-        else:
-            body = " ".join(rng.choice(words, size=n_words))
-        return tok.encode(render_chat([{"role": "user", "content": body}], tok))
-
+    make_prompt = prompt_maker(args, tok, np.random.default_rng(1234 + int(os.environ.get("RANK", "0"))))
     phase = args.phases.split(",")[0]
     if SAMPLING[phase].get("json"):
         raise SystemExit("the json phase needs the HTTP path (response_format is an API-level option)")

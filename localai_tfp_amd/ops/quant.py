@@ -557,19 +557,23 @@ def random_quantized(rng: np.random.Generator, qtype: int, n_rows: int, row_len:
 
 def repack_q6_k(raw: np.ndarray, n_rows: int, row_len: int):
     """ggml Q6_K -> (blocks [n_rows, nblk*208] uint8, d [n_rows, nblk] fp16-as-uint16)."""
-    q, sc, d = q6k_codes(raw)
-    nb = q.shape[0]
-    qg = q.reshape(nb, 4, 64)  # quarter g -> 64 elements
-    lo = (qg & 0xF)
-    hi = qg >> 4
+    # Per block the 256 codes q (q6k_codes) fall into quarters g of 64; quarter g stores ql[g][i] = lo(q[64g + i]) |
+    # lo(q[64g + 32 + i]) << 4 (i < 32) and qh[g][i] = the 2 high bits of q[64g + 16s + i] at bit 2s (s < 4, i < 16).
+    # ggml keeps code 128n + 32c + j as nibble c >> 1 of ql[64n + 32(c & 1) + j] and bits 2c of qh[32n + j], so both
+    # planes are byte shuffles of ggml's: done on the bytes (a multi-GB model repacks in about a second; going
+    # through one int32 per code took several)
+    b = _blocks(raw, QType.Q6_K)
+    nb = b.shape[0]
     out = np.empty((nb, 208), np.uint8)
-    ql = (lo[:, :, 0:32] | (lo[:, :, 32:64] << 4)).astype(np.uint8)  # [nb, 4, 32]
-    out[:, 0:128] = ql.reshape(nb, 128)
-    h4 = hi.reshape(nb, 4, 4, 16)  # [nb, g, s, i]
-    qh = (h4[:, :, 0] | (h4[:, :, 1] << 2) | (h4[:, :, 2] << 4) | (h4[:, :, 3] << 6)).astype(np.uint8)
-    out[:, 128:192] = qh.reshape(nb, 64)
-    out[:, 192:208] = sc.view(np.uint8)
-    dd = d.astype(np.float16).view(np.uint16)
+    for n in range(2):
+        x, y = b[:, 64 * n:64 * n + 32], b[:, 64 * n + 32:64 * n + 64]  # ggml ql: low nibbles = quarter 2n
+        out[:, 64 * n:64 * n + 32] = (x & 0x0F) | ((y & 0x0F) << 4)
+        out[:, 64 * n + 32:64 * n + 64] = (x >> 4) | (y & 0xF0)
+        x, y = b[:, 128 + 32 * n:144 + 32 * n], b[:, 144 + 32 * n:160 + 32 * n]  # ggml qh
+        out[:, 128 + 32 * n:144 + 32 * n] = (x & 0x03) | ((y & 0x03) << 2) | ((x & 0x0C) << 2) | ((y & 0x0C) << 4)
+        out[:, 144 + 32 * n:160 + 32 * n] = ((x >> 4) & 0x03) | ((y >> 2) & 0x0C) | ((x >> 2) & 0x30) | (y & 0xC0)
+    out[:, 192:208] = b[:, 192:208]
+    dd = _f16(b[:, 208:210].copy()).astype(np.float16).view(np.uint16)
     nblk = row_len // 256
     return out.reshape(n_rows, nblk * 208), dd.reshape(n_rows, nblk)
 
